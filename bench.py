@@ -16,7 +16,14 @@ Inputs are resident in HBM before timing.  One step = plan (decoded sizes + scan
 (CRC32 verify, decompress, offset checks, row descriptors) over the rank's whole shard.
 value = decoded bytes of all ranks per second (GiB = 2^30) over the slowest rank's time.
 
-Run: python bench.py [--gpus N --steps K --warmup W] [--workload configs3]
+A plain run does what the headline needs and no more: it generates and uploads the blocks, warms
+up, checks every block's status, times the K steps and prints the result line.  --full adds what
+the line reported before the option existed: the blocks verified against the generator, the
+measured copy rate, host_io, the extra legs (codec_none, configs4_zstd, kv100_*, configs2_encode,
+compaction, per_call, configs0) and the CPU baselines; the --no-* switches trim a --full run.
+--dump-outputs DIR writes what the last timed step left in the caller's buffers (dump_outputs).
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--workload configs3] [--full] [--dump-outputs DIR]
      python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -54,8 +61,15 @@ def parse():
     p.add_argument("--codec", choices=["snappy", "none", "lz4", "zstd"], default="snappy",
                    help="zstd runs BASELINE configs[4] (1 KiB values, Zipf-prefixed keys, libzstd level 3 + checksum)")
     p.add_argument("--values", choices=["half", "rand"], default="half")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline: verification against the generator, measured copy rate, "
+                        "host_io, the extra legs and the CPU baselines (a plain run has none of them)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy (dump_outputs; "
+                        "under torchrun, rank 0's shard)")
     p.add_argument("--verify", choices=["all", "sample", "none"], default="",
-                   help="decoded bytes, meta and rows vs the generator (default: all for configs1, sample for configs3)")
+                   help="decoded bytes, meta and rows vs the generator (default with --full: all for configs1, "
+                        "sample for configs3; without --full: none)")
     p.add_argument("--cpu-seconds", type=float, default=8.0, help="budget per CPU-baseline leg")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cache", default="", help="configs[4]: directory to reuse the generated workload from")
@@ -162,13 +176,14 @@ def main():
         leg.step()
     torch.cuda.synchronize(device)
 
-    # ---- verify, outside the timed region: every block's status; decoded bytes, meta and row
-    # descriptors against the generator for every block (configs1) or evenly spread chunks (configs3)
+    # ---- verify, outside the timed region: every block's status (its lengths give the decoded
+    # bytes `value` counts); with --full or --verify, decoded bytes, meta and row descriptors against
+    # the generator for every block (configs1) or evenly spread chunks (configs3)
     meta = leg.d_meta.download().view(sc.META_DTYPE)
     assert (meta["status"] == 0).all(), np.unique(meta["status"], return_counts=True)
     dec_bytes = int(np.sum(meta["data_len"].astype(np.int64) + 2 * meta["n_rows"].astype(np.int64) + 2))
     n_rows = int(meta["n_rows"].astype(np.int64).sum())
-    verify = args.verify or ("all" if args.workload == "configs1" else "sample")
+    verify = args.verify or (("all" if args.workload == "configs1" else "sample") if args.full else "none")
     verified = 0
     if shard is not None and verify != "none":
         verified = leg.verify_against_generator(wl, shard, verify, meta, threads, half)
@@ -193,6 +208,9 @@ def main():
 
     ms_per_step = elapsed * 1e3 / args.steps
     value = job_dec_bytes * args.steps / elapsed / 2**30
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sc, leg)
 
     # roofline of the dominant kernel: algorithmic bytes per launch / its event time
     roofline = decode_roofline(enc_bytes, n, dec_bytes, n_rows, kern_ms)
@@ -228,26 +246,29 @@ def main():
                 ", every block generated on its own: tools/benchgen.c bg_build_set)")
     result = {"metric": METRIC, "value": round(value, 2), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
               "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-              "scaling": scaling, "vs_baseline": None, "dtype": "u8", "data": data,
+              "scaling": scaling, "vs_baseline": None, "dtype": "u8", "full": args.full, "data": data,
               "config": {"workload": workload, "blocks_per_gpu": n, "set_blocks": set_blocks, "codec": args.codec,
                          "values": args.values, "block_size": 4096, "decoded_bytes_per_gpu": dec_bytes,
                          "encoded_bytes_per_gpu": enc_bytes, "rows_per_gpu": n_rows,
                          "parallelism": f"shard{world} round-robin (no collective)"},
               "roofline": roofline,
               "verified": {"blocks": verified, "mode": verify if shard is not None else "status only",
-                           "what": "every block's status; decoded bytes, meta and row descriptors vs the generator"}}
+                           "what": "every block's status" + ("" if verify == "none" else
+                                                             "; decoded bytes, meta and row descriptors vs the generator")}}
 
-    if rank == 0 and world == 1:
+    # ---- everything below runs with --full only: each takes runs of its own
+    solo_full = args.full and rank == 0 and world == 1
+    if solo_full:
         # the kernel's rate against a device-to-device copy measured on this box too
         copy = measured_copy_gbps(device)
         roofline["measured_copy_GBps"] = copy["value"]
         roofline["measured_copy"] = copy
         roofline["frac_of_measured_copy"] = round(roofline["achieved"] / copy["value"], 4)
 
-    if rank == 0 and world == 1 and not args.no_host_io and shard is not None:
+    if solo_full and not args.no_host_io and shard is not None:
         result["host_io"] = host_io_rate(sc, ctx, codec, blob, in_off)
 
-    if rank == 0 and world == 1 and not args.no_extras and args.codec == "snappy" and args.workload == "configs1":
+    if solo_full and not args.no_extras and args.codec == "snappy" and args.workload == "configs1":
         del leg  # the extra legs get the HBM back
         result["codec_none"] = codec_none_leg(sc, ctx, stream, wl, args, threads)
         result["configs4_zstd"] = zstd_leg(sc, ctx, stream, wl, args, threads)
@@ -264,7 +285,7 @@ def main():
         result["per_call"] = pb.per_call(ctx, sc, ob, wl, 300)
         result["configs0"] = pb.configs0(ctx, sc, ob)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if solo_full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(codec, blob, in_off, args.cpu_seconds)
 
     if rank == 0:
@@ -363,6 +384,54 @@ class DecodeLeg:
         for b in (self.d_in, self.d_in_off, self.d_out_off, self.d_row_base, self.d_scratch, self.d_out, self.d_meta,
                   self.d_rows):
             b.free()
+
+
+DUMP_BUDGET = 64_000_000  # bytes of .npy files --dump-outputs may write in all
+DUMP_SAMPLE_BLOCKS = 2048
+DUMP_ALL_BLOCKS = 1_000_000
+
+
+def dump_outputs(out_dir, sc, leg):
+    """What the last timed step left in the buffers a caller of slate_block_decode_plan_device +
+    slate_block_decode_device receives, as out_dir/<name>.npy (float32 where every value is below
+    2^24, else float64; at most DUMP_BUDGET bytes in all).  The inputs are seeded, so two builds
+    run with the same arguments write comparable files:
+      blocks_all    [m, 3] status, data_len, n_rows of the first m = min(n, DUMP_ALL_BLOCKS) blocks
+      block_index   [S]    a fixed seeded sample of blocks, ascending; the arrays below are theirs
+      out_off, row_base [S + 1]  each sampled block's plan entry, then entry n (the totals)
+      meta          [S, 6] status, flags, detail, data_len, n_rows, aux
+      decoded       the sampled blocks' decoded bytes, one after the other
+      rows          [R, 7] the sampled blocks' n_rows row descriptors, one block after the other:
+                    row_off, key_prefix_len, key_suffix_len, value_len, flags, meta_len, status"""
+    n = leg.n
+    os.makedirs(out_dir, exist_ok=True)
+    meta = leg.d_meta.download().view(sc.META_DTYPE)
+    out_off = leg.d_out_off.download(dtype=np.uint64)
+    row_base = leg.d_row_base.download(dtype=np.uint64)
+    dec_len = meta["data_len"].astype(np.int64) + 2 * meta["n_rows"].astype(np.int64) + 2
+    m = min(n, DUMP_ALL_BLOCKS)
+    arrays = {"blocks_all": np.stack([meta[f][:m].astype(np.float32) for f in ("status", "data_len", "n_rows")], axis=1)}
+    # the sample's size from the budget left: 4 B per decoded byte, 7 x 4 B per row, 9 x 8 B of plan and meta
+    per_block = (4 * int(dec_len.sum()) + 28 * int(meta["n_rows"].astype(np.int64).sum())) / max(n, 1) + 72
+    s = max(0, min(n, DUMP_SAMPLE_BLOCKS, int(0.9 * (DUMP_BUDGET - arrays["blocks_all"].nbytes) / per_block)))
+    idx = np.sort(np.random.default_rng(SEED).choice(n, size=s, replace=False)) if s else np.zeros(0, np.int64)
+    dec, rows = [], []
+    for k in idx:
+        k = int(k)
+        dec.append(leg.d_out.download(int(dec_len[k]), int(out_off[k])))
+        rows.append(leg.d_rows.download(16 * int(meta["n_rows"][k]), 16 * int(row_base[k])).view(sc.ROW_DTYPE))
+    rows = np.concatenate(rows) if rows else np.zeros(0, sc.ROW_DTYPE)
+    with_total = np.append(idx, n)
+    arrays["block_index"] = idx.astype(np.float64)
+    arrays["out_off"] = out_off[with_total].astype(np.float64)
+    arrays["row_base"] = row_base[with_total].astype(np.float64)
+    arrays["meta"] = np.stack([meta[f][idx].astype(np.float64) for f in sc.META_DTYPE.names], axis=1).reshape(s, 6)
+    arrays["decoded"] = (np.concatenate(dec) if dec else np.zeros(0, np.uint8)).astype(np.float32)
+    arrays["rows"] = np.stack([rows[f].astype(np.float32) for f in sc.ROW_DTYPE.names], axis=1).reshape(len(rows), 7)
+    total = sum(a.nbytes + 128 for a in arrays.values())
+    assert total <= DUMP_BUDGET, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def decode_roofline(enc_bytes, n, dec_bytes, n_rows, kern_ms):

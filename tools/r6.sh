@@ -4,7 +4,7 @@
 #   tests       the GPU suite (pytest -m gpu)
 #   testsk      a subset: TESTK = pytest -k expression
 #   smoke       __graft_entry__.smoke()
-#   bench       the default bench line
+#   bench       the bench line with every leg (bench.py --full)
 #   head        the headline leg alone under rocprofv3 --kernel-trace --stats
 #   percall     tools/percall_bench.py (per-call decode / seek / reader from C)
 #   ab          tools/lib_ab.py AB_BLOCKS (1048576) blocks, AB_ROUNDS (3) rounds over LIBS (file names
@@ -29,7 +29,7 @@ for s in ${STEPS:-tests}; do
     timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 || { echo SMOKE_FAILED; tail -20 $OUT/smoke.log; exit 1; }
     tail -1 $OUT/smoke.log ;;
   bench)
-    timeout -k 10 900 python -u bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -30 $OUT/bench.err; exit 1; }
+    timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -30 $OUT/bench.err; exit 1; }
     cat $OUT/bench.json ;;
   head)
     timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/headprof -o head -- python3 bench.py --no-cpu-baseline --no-host-io --no-extras --verify none > $OUT/head.json 2> $OUT/head.err || { echo HEAD_PROF_FAILED; tail -30 $OUT/head.err; exit 1; }
