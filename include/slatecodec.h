@@ -496,6 +496,97 @@ int slate_bloom_decode(slate_ctx* ctx, const uint8_t* buf, size_t len, int codec
 int slate_bloom_has_keys(slate_ctx* ctx, uint16_t num_probes, const uint8_t* bits, size_t bits_len,
                          const uint8_t* keys, const uint64_t* key_off, uint64_t n, uint8_t* out);
 
+/* ---- batched point reads: DB.GetWithOptions' SST part (slatedb/db.go:237-250) ----------
+ * A GPU cannot win one point read against a CPU; it can win a batch of them.  An SST is opened
+ * once into HBM, and one call then answers n keys over a list of such handles exactly as Go's Get
+ * would answer each key:
+ *   1. sstMayIncludeKey (db.go:291-301): RangeCoversKey (internal/sstable/table.go:89-94: false
+ *      when Info.FirstKey is empty or key < FirstKey), then ReadFilter (decode.go:50-71): a filter
+ *      that is present and decodes answers HasKey(key); an absent (FilterLen < 1) or undecodable
+ *      one means "may include";
+ *   2. sstable.NewIteratorAtKey (internal/sstable/iterator.go:43-57): nextBlock =
+ *      firstBlockIncludingOrAfterKey(index, key);
+ *   3. iter.Next (iterator.go:59-89): no block left -> no row.  Else block nextBlock is read and
+ *      decoded (a ReadRange or block.Decode error ends the iteration: no row, no further block),
+ *      block.NewIteratorAtKey seeks it (block/iterator.go:31-82, an error again ends it), and
+ *      blockIter.Next (:84-107) returns the row it stands on -- or, when it stands past the last
+ *      row or the row fails v0RowCodec.Decode against the iterator's firstKey, the iteration goes
+ *      on with the next block, where the seek runs again;
+ *   4. db.go:245-248: a row whose key equals the key ends the whole search (checkValue: a
+ *      tombstone is ErrKeyNotFound, else the value); any other row, or none, falls through to the
+ *      next SST.  The iterator's warnings are never read.
+ *
+ * slate_sst_handle: one encoded SST held in HBM of the context's GPU.  slate_sst_open takes the whole object from host
+ * memory, reads the info, index and filter as slate_sst_read_info, slate_decode_index and
+ * slate_bloom_decode do (an info or index error is returned and no handle is made; a filter that
+ * fails bloom.Decode or whose range is invalid leaves the handle without one, its status in
+ * *filter_status), and uploads the data blocks.  A block's byte range is [Offset(i), Offset(i+1))
+ * and the last block's ends at Info.FilterOffset (getBlockRange, decode.go:93-103); a range
+ * bytesBlob.ReadRange rejects (blob.go:23-26: inverted, or past the object) is remembered as
+ * SLATE_E_BLOB_RANGE for that block and never read.
+ * HBM per handle: the bytes from the lowest valid block start to the highest valid block end (for
+ * a well-formed SST: every data block, once) + 17 bytes per block (two u64 range ends, a flag)
+ * + the index's first keys + 8 bytes per block for their offsets + the decoded filter bits + the
+ * info's first key, each rounded up to 256 bytes; *device_bytes returns the sum.  Allocation
+ * failure: SLATE_E_OOM.  A handle is used only with contexts of its device; slate_sst_close waits
+ * for the device. */
+typedef struct slate_sst_handle slate_sst_handle;
+int slate_sst_open(slate_ctx* ctx, const uint8_t* sst, size_t sst_len, slate_sst_handle** h);
+void slate_sst_close(slate_sst_handle* h);
+/* Every output may be NULL.  first_key_cap too small: SLATE_E_CAPACITY (info->first_key_len set). */
+int slate_sst_handle_info(const slate_sst_handle* h, slate_sst_info* info, uint8_t* first_key, size_t first_key_cap,
+                          uint64_t* n_blocks, int* filter_present, int* filter_status, uint64_t* device_bytes);
+
+enum slate_get_outcome {
+  SLATE_GET_MISS = 0,      /* no handle returned a row with this key (ErrKeyNotFound after the last SST) */
+  SLATE_GET_VALUE = 1,     /* handle `sst` returned the key with a value */
+  SLATE_GET_TOMBSTONE = 2, /* handle `sst` returned the key as a tombstone: ErrKeyNotFound, search ended */
+  SLATE_GET_PANIC = 3,     /* Go would panic in handle `sst`: err = SLATE_E_BLOCK_FIRSTKEY_PANIC (7),
+                              SLATE_E_ROW_PANIC (27) or SLATE_E_SEEK_PANIC (64); search ended */
+};
+enum slate_get_stage {     /* how far the lookup went in the handle it ended in */
+  SLATE_GET_AT_RANGE = 0,  /* RangeCoversKey said no */
+  SLATE_GET_AT_FILTER = 1, /* the filter said no */
+  SLATE_GET_AT_END = 2,    /* iter.Next ran out of blocks */
+  SLATE_GET_AT_ERROR = 3,  /* a block read, block.Decode or block.NewIteratorAtKey error (or panic) ended it */
+  SLATE_GET_AT_ROW = 4,    /* iter.Next returned row `row` of block `block` (or panicked decoding it) */
+};
+typedef struct slate_get_result { /* 24 bytes */
+  uint8_t outcome;    /* slate_get_outcome */
+  uint8_t stage;      /* slate_get_stage, in handle `sst` when one answered, else in the last handle consulted */
+  int16_t err;        /* first non-OK status met for this key, handles in precedence order (a block's read /
+                         decode / seek status, or a row's decode status on the way to the next block);
+                         SLATE_OK if none.  A panic's status replaces it. */
+  uint32_t sst;       /* handle that answered (VALUE / TOMBSTONE / PANIC); n_sst for a MISS */
+  uint32_t err_sst;   /* handle in which err was met (0 when err is SLATE_OK) */
+  uint32_t block;     /* stage AT_ROW: where iter.Next's row came from; 0 otherwise */
+  uint32_t row;
+  uint32_t value_len; /* VALUE: bytes of the value; 0 otherwise */
+} slate_get_result;
+/* n keys (key i = keys[key_off[i]..key_off[i+1])) against n_sst handles in precedence order, each
+ * treated as db.go:238-250 treats an L0 SST; key i is looked up in handle j+1 only while every
+ * handle up to j gave no row with its key.  Host buffers in and out, synchronous.  res (n) and
+ * val_off (n+1) are always filled; the values come back concatenated in query order, value i =
+ * vals[val_off[i]..val_off[i+1]).  If vals_cap < val_off[n], or vals is NULL with val_off[n] > 0,
+ * no value is copied and the call returns SLATE_E_CAPACITY (the retry looks the keys up again).
+ * n == 0 is SLATE_OK.  Sorted runs (SortedRun.SstWithKey) and device-resident keys are out of scope.
+ * CodecNone handles -- the DB's default codec -- take a fused kernel: one wave per query checks
+ * the block's CRC over the encoded bytes in place, runs block.Decode's checks, the seek, the row
+ * decode and the key compare, and walks on to the next block itself; nothing is gathered or
+ * decoded into a buffer.  Blocks with more than 2048 rows, and every other codec, take the
+ * general path: the blocks the batch touches are gathered, decoded once each as one batch by the
+ * block decode kernels, sought and fetched, in rounds until no query is pending. */
+int slate_sst_get_batch(slate_ctx* ctx, slate_sst_handle* const* ssts, uint32_t n_sst, const uint8_t* keys,
+                        const uint64_t* key_off, uint64_t n, slate_get_result* res, uint8_t* vals, uint64_t vals_cap,
+                        uint64_t* val_off);
+/* Observability (no Go counterpart), summed over this context's get_batch calls since the last
+ * reset: queries finished by the fused kernel, queries handed to the general path (every query of
+ * a non-CodecNone handle that reaches a block, and a fused query that met a block the fused kernel
+ * refuses), kernel rounds (one per fused launch, one per general decode round) and blocks handed
+ * to the block decode kernels.  Any pointer may be NULL. */
+int slate_sst_get_counters(slate_ctx* ctx, uint64_t* n_fused, uint64_t* n_general, uint64_t* n_rounds,
+                           uint64_t* n_blocks_decoded, int reset);
+
 /* ---- compaction merge (iter.MergeSort, internal/iter/merge.go:12-111) ----------------- */
 /* k sorted iterators, concatenated: key i = keys[key_off[i]..key_off[i+1]), iterator j holds
  * elements [src_start[j], src_start[j+1]) (src_start: k+1 host values, src_start[0] = 0,

@@ -296,6 +296,24 @@ struct slate_ctx {
   } zl_plan;
   bool zl_armed = false;
   DevBuf x_words, x_enc, x_slots, x_asm, x_crc, x_bkt;
+  // slate_sst_get_batch (api_get.cpp): the call's queries and their state, the general path's
+  // per-round buffers (outs: one decoded-bytes buffer per round, kept until the values are copied)
+  struct GetBufs {
+    DevBuf keys, koff, res, vsrc, qblk, act0, act1, pend0, pend1, gen, seek, cnt, voff, part, vals;
+    DevBuf bflag, bdata, bmeta, list, in_off, gin, out_off, row_base, scr, meta, rows;
+    std::vector<DevBuf> outs;
+    PinBuf h_cnt;
+    uint64_t n_fused = 0, n_general = 0, n_rounds = 0, n_blocks_decoded = 0;
+    void release() {
+      for (DevBuf* b : {&keys, &koff, &res, &vsrc, &qblk, &act0, &act1, &pend0, &pend1, &gen, &seek, &cnt, &voff,
+                        &part, &vals, &bflag, &bdata, &bmeta, &list, &in_off, &gin, &out_off, &row_base, &scr, &meta,
+                        &rows})
+        b->release();
+      for (DevBuf& b : outs) b.release();
+      outs.clear();
+      h_cnt.release();
+    }
+  } get;
   std::shared_ptr<SegPool> seg_pool = std::make_shared<SegPool>();
   // device time of the builder's GPU passes (slate_ctx_set_timing): nanoseconds, summed over the
   // kernel groups of every stream the context uses (GpuSpan)
@@ -359,6 +377,7 @@ struct slate_ctx {
     d2h_after = nullptr;
     h_small.release();
     h_seek.release();
+    get.release();
   }
 };
 

@@ -322,6 +322,69 @@ hipError_t launch_block_seek(hipStream_t st, const uint8_t* data, const uint64_t
 hipError_t launch_index_seek(hipStream_t st, const uint8_t* keys, const uint64_t* key_off, uint64_t n_blocks,
                              const uint8_t* qkeys, const uint64_t* qkey_off, uint64_t nq, uint64_t* out);
 
+// ---------------------------------------------------------------- batched point reads (get.hip)
+// One SST handle as the kernels see it (slate_sst_handle's device arrays, api_get.cpp).
+struct GetSst {
+  const uint8_t* region;      // the data blocks; block b = region[bstart[b] .. bend[b])
+  const uint64_t* bstart;     // nb
+  const uint64_t* bend;       // nb
+  const uint8_t* bbad;        // nb: 1 = bytesBlob.ReadRange rejects the block's range (never read)
+  const uint8_t* ikeys;       // the index's first keys, key b = ikeys[ikey_off[b] .. ikey_off[b+1])
+  const uint64_t* ikey_off;   // nb + 1
+  const uint8_t* fbits;       // decoded filter bits (has_filter)
+  const uint8_t* first_key;   // Info.FirstKey
+  uint64_t fbits_len;
+  uint32_t nb;
+  uint32_t num_probes;
+  uint32_t has_filter;
+  uint32_t first_key_len;
+  uint32_t sst;               // the handle's place in the call's list
+};
+// The queries of one call and their state, in device memory.
+struct GetQ {
+  const uint8_t* keys;
+  const uint64_t* key_off;    // n + 1
+  uint64_t n;
+  slate_get_result* res;      // n
+  uint64_t* vsrc;             // n: device address of a VALUE's bytes
+  uint32_t* qblk;             // n: the block a pending query reads next (kGetDone: finished)
+};
+constexpr uint32_t kGetDone = 0xFFFFFFFFu;
+// counters of a call (u32 words in device memory, zeroed by the host where it says so)
+enum { kGcPend = 0, kGcGen = 1, kGcBlocks = 2, kGcAct = 3, kGcFused = 4, kGcBytesLo = 5, kGcBytesHi = 6, kGcWords = 8 };
+hipError_t launch_get_init(hipStream_t st, const GetQ& q, uint32_t n_sst);
+// sstMayIncludeKey + firstBlockIncludingOrAfterKey for the active queries (act == nullptr: all n):
+// a stage, or qblk and an entry of pend (cnt[kGcPend] counts them)
+hipError_t launch_get_locate(hipStream_t st, const GetSst& s, const GetQ& q, const uint32_t* act, uint64_t na,
+                             uint32_t* pend, uint32_t* cnt);
+// the fused CodecNone path over pend[0..np): finished queries counted in cnt[kGcFused], the rest
+// appended to gen (cnt[kGcGen]) with qblk = the block the fused kernel refused
+hipError_t launch_get_fused(hipStream_t st, const GetSst& s, const GetQ& q, const uint32_t* pend, uint32_t np,
+                            uint32_t* gen, uint32_t* cnt, int num_cus);
+// general path, one round over pend[0..np): mark the blocks to decode (bflag 0 -> 1; queries past
+// the last block or on a rejected range finish here), compact them in block order (list, in_off,
+// cnt[kGcBlocks], their bytes in cnt[kGcBytesLo / Hi]), gather their bytes back to back, publish the decoded blocks (bflag 2, bdata,
+// bmeta), then seek + fetch (pending queries appended to pend_next, cnt[kGcPend])
+hipError_t launch_get_mark(hipStream_t st, const GetSst& s, const GetQ& q, const uint32_t* pend, uint32_t np,
+                           uint32_t* bflag);
+hipError_t launch_get_compact(hipStream_t st, const GetSst& s, const uint32_t* bflag, uint32_t* list, uint64_t* in_off,
+                              uint32_t* cnt);
+hipError_t launch_get_gather(hipStream_t st, const GetSst& s, const uint32_t* list, const uint64_t* in_off, uint32_t nc,
+                             uint8_t* gin);
+hipError_t launch_get_publish(hipStream_t st, const uint32_t* list, uint32_t nc, const uint8_t* out,
+                              const uint64_t* out_off, const slate_block_meta* meta, uint32_t* bflag, uint64_t* bdata,
+                              slate_block_meta* bmeta);
+hipError_t launch_get_fetch(hipStream_t st, const GetSst& s, const GetQ& q, const uint32_t* pend, uint32_t np,
+                            const uint64_t* bdata, const slate_block_meta* bmeta, slate_seek* seek, uint32_t* pend_next,
+                            uint32_t* cnt);
+// the queries of act (nullptr: all n) that are still a MISS, for the next handle (cnt[kGcAct])
+hipError_t launch_get_active(hipStream_t st, const GetQ& q, const uint32_t* act, uint64_t na, uint32_t* act_next,
+                             uint32_t* cnt);
+// val_off (n + 1) = exclusive scan of the value lengths (part: get_scan_parts(n) u64), then the copy
+size_t get_scan_parts(uint64_t n);
+hipError_t launch_get_val_scan(hipStream_t st, const GetQ& q, uint64_t* val_off, uint64_t* part);
+hipError_t launch_get_copy(hipStream_t st, const GetQ& q, const uint64_t* val_off, uint8_t* vals);
+
 // CodecLz4 index / filter payloads split by (independent) data block: blk = nblk x (frame offset,
 // block size word); one wave per block in LDS; sizes[k] = decoded bytes at slots + k * 64 KiB, or
 // ~0u for a block the serial path must decode (decode.hip).

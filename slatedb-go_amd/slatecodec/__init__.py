@@ -39,6 +39,11 @@ SEEK_DTYPE = np.dtype([("start", "<u4"), ("first_idx", "<i4"), ("n_warn", "<u4")
                        ("first_len", "<u2")])
 META_DTYPE = np.dtype([("status", "<i2"), ("flags", "<u2"), ("detail", "<i4"), ("data_len", "<u4"),
                        ("n_rows", "<u2"), ("aux", "<u2")])
+# slate_get_result (24 bytes) and its enums
+GET_DTYPE = np.dtype([("outcome", "u1"), ("stage", "u1"), ("err", "<i2"), ("sst", "<u4"), ("err_sst", "<u4"),
+                      ("block", "<u4"), ("row", "<u4"), ("value_len", "<u4")])
+GET_MISS, GET_VALUE, GET_TOMBSTONE, GET_PANIC = 0, 1, 2, 3
+GET_AT_RANGE, GET_AT_FILTER, GET_AT_END, GET_AT_ERROR, GET_AT_ROW = 0, 1, 2, 3, 4
 ROW_DTYPE = np.dtype([("row_off", "<u4"), ("key_prefix_len", "<u2"), ("key_suffix_len", "<u2"),
                       ("value_len", "<u4"), ("flags", "u1"), ("meta_len", "u1"), ("status", "<i2")])
 
@@ -158,6 +163,12 @@ _SIGS = {
     "slate_merge_sorted_device": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
     "slate_kv_scratch_bytes": (C.c_size_t, [C.c_uint64]),
     "slate_index_block_offsets": (C.c_int, [vp, vp, C.c_size_t]),
+    "slate_sst_open": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(vp)]),
+    "slate_sst_close": (None, [vp]),
+    "slate_sst_handle_info": (C.c_int, [vp, C.POINTER(SstInfo), vp, C.c_size_t, u64p, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), u64p]),
+    "slate_sst_get_batch": (C.c_int, [vp, C.POINTER(vp), C.c_uint32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp]),
+    "slate_sst_get_counters": (C.c_int, [vp, u64p, u64p, u64p, u64p, C.c_int]),
     "slate_rows_kv_lengths_device": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     "slate_rows_kv_copy_device": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     "slate_kv_gather_lengths_device": (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]),
@@ -324,6 +335,44 @@ class Context:
         _check(lib().slate_index_seek(self._h, index.handle, _ptr(kd), _ptr(ko), len(keys), _ptr(out)),
                "slate_index_seek")
         return out[: len(keys)]
+
+    # ------------------------------------------------------------ batched point reads
+    def open_sst(self, sst: bytes) -> "SstHandle":
+        """slate_sst_open: the encoded SST held in HBM of this context's GPU."""
+        return SstHandle(self, sst)
+
+    def get_into(self, handles: list["SstHandle"], keys: list[bytes], vals_cap: int | None):
+        """slate_sst_get_batch with a caller-chosen value capacity (None: no value buffer) ->
+        (status, res, vals, val_off): the capacity protocol as a C caller sees it."""
+        kd, ko = _arena(keys)
+        n = len(keys)
+        res = np.zeros(max(n, 1), GET_DTYPE)
+        val_off = np.zeros(n + 1, np.uint64)
+        vals = np.zeros(max(vals_cap or 0, 1), np.uint8)
+        hs = (vp * max(len(handles), 1))(*[h.handle for h in handles])
+        st = lib().slate_sst_get_batch(self._h, hs, len(handles), _ptr(kd), _ptr(ko), n, _ptr(res),
+                                       _ptr(vals) if vals_cap is not None else None, vals_cap or 0, _ptr(val_off))
+        return st, res[:n], vals[: vals_cap or 0], val_off
+
+    def get(self, handles: list["SstHandle"], keys: list[bytes]):
+        """DB.Get's SST part for every key over `handles` in precedence order -> (res GET_DTYPE[n],
+        vals u8, val_off u64[n + 1]); key i's value is vals[val_off[i]:val_off[i + 1]]."""
+        # first try: 128 bytes per key, or what the context's last get needed per key if that was more
+        per_key = max(128, getattr(self, "_get_bytes_per_key", 0))
+        st, res, vals, val_off = self.get_into(handles, keys, per_key * len(keys))
+        if keys:
+            self._get_bytes_per_key = -(-int(val_off[len(keys)]) // len(keys))
+        if st == E_CAPACITY:  # the exact size is in val_off[n]; the keys are looked up again
+            st, res, vals, val_off = self.get_into(handles, keys, int(val_off[len(keys)]))
+        _check(st, "slate_sst_get_batch")
+        return res, vals[: int(val_off[len(keys)])], val_off
+
+    def get_counters(self, reset: bool = False) -> dict:
+        """slate_sst_get_counters -> {n_fused, n_general, n_rounds, n_blocks_decoded}."""
+        v = [C.c_uint64() for _ in range(4)]
+        _check(lib().slate_sst_get_counters(self._h, *[C.byref(x) for x in v], 1 if reset else 0),
+               "slate_sst_get_counters")
+        return dict(zip(("n_fused", "n_general", "n_rounds", "n_blocks_decoded"), (x.value for x in v)))
 
     def block_decode(self, encoded: bytes, codec: int):
         """block.Decode(&b, input, codec) -> (status, meta, Data, Offsets)."""
@@ -717,6 +766,47 @@ class Index:
             _check(lib().slate_index_block_meta(self._h, i, C.byref(off), C.byref(p), C.byref(ln)), "block_meta")
             out.append((off.value, C.string_at(p.value, ln.value) if ln.value else b""))
         return out
+
+
+class SstHandle:
+    """slate_sst_handle: one encoded SST opened into HBM (Context.open_sst)."""
+
+    def __init__(self, ctx: "Context", sst: bytes):
+        a = np.frombuffer(bytes(sst) or b"\0", dtype=np.uint8)
+        h = vp()
+        _check(lib().slate_sst_open(ctx.handle, _ptr(a), len(sst), C.byref(h)), "slate_sst_open")
+        self._h = h.value
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        """slate_sst_handle_info -> info fields, first_key, n_blocks, filter_present, filter_status,
+        device_bytes."""
+        inf = SstInfo()
+        nb, db = C.c_uint64(), C.c_uint64()
+        fp, fs = C.c_int(), C.c_int()
+        _check(lib().slate_sst_handle_info(self._h, C.byref(inf), None, 0, C.byref(nb), C.byref(fp), C.byref(fs),
+                                           C.byref(db)), "slate_sst_handle_info")
+        fk = np.zeros(max(inf.first_key_len, 1), np.uint8)
+        _check(lib().slate_sst_handle_info(self._h, None, _ptr(fk), fk.size, None, None, None, None),
+               "slate_sst_handle_info")
+        d = {f: getattr(inf, f) for f, _ in SstInfo._fields_}
+        d.update(first_key=fk[: inf.first_key_len].tobytes(), n_blocks=nb.value, filter_present=fp.value,
+                 filter_status=fs.value, device_bytes=db.value)
+        return d
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().slate_sst_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except (TypeError, AttributeError):  # interpreter shutdown: module globals already gone
+            pass
 
 
 class SstBuilder:
