@@ -30,6 +30,25 @@ PANICS = (7, 27, 64)
 FIELDS = ("outcome", "stage", "err", "sst", "err_sst", "block", "row", "value_len")
 
 
+MAX_DECODE_CAP = 1 << 24
+
+
+def decode_cap(enc: bytes, codec: int) -> int:
+    """Room for block.Decode's output, sized from the block itself as the decode plan sizes it (the
+    frame's own length: Snappy's prefix, the LZ4 / Zstd frame walk, Zlib's stream length), never
+    less than ob.block_decode's default of 24 x the encoded length -- so a block that compresses
+    better than 24:1 decodes instead of failing for room (Go's decoders grow their output).  A
+    corrupt block may claim any length; past MAX_DECODE_CAP the claim is not followed."""
+    cap = max(len(enc) * 24, 64)
+    if len(enc) >= 6:
+        h, p = ob._buf(enc)
+        dl = ob.C.c_uint64(0)
+        ob.lib().or_decompress_len(codec, p, len(enc) - 4, ob.C.byref(dl))
+        if cap < dl.value + 16 <= MAX_DECODE_CAP:
+            cap = dl.value + 16
+    return cap
+
+
 class RefSst:
     """What slate_sst_open reads of one encoded SST (open_status != 0: no handle is made)."""
 
@@ -78,7 +97,8 @@ class RefSst:
             if start > len(self.sst) or end > len(self.sst) or start > end:
                 self.blocks[b] = (E_BLOB_RANGE, b"", [])
             else:
-                m, out, _ = ob.block_decode(self.sst[start:end], self.codec)
+                enc = self.sst[start:end]
+                m, out, _ = ob.block_decode(enc, self.codec, decode_cap(enc, self.codec))
                 if m["status"]:
                     self.blocks[b] = (m["status"], b"", [])
                 else:

@@ -1,9 +1,9 @@
 """GPU parity of the batched point reads (slate_sst_open / slate_sst_get_batch) with the
 reference composed from the oracle (tests/getref.py): every field of every result, the value
 offsets and the value bytes, on clean SSTs of the five codecs and on SSTs with a missing or
-corrupt filter, a corrupt index, corrupt blocks and rows, an inverted block range, a block with
-more rows than the fused kernel takes, several handles in precedence order, and the capacity
-protocol; the counters as conditions on the paths taken."""
+corrupt filter, a corrupt index, corrupt blocks (every codec) and rows, an inverted block range,
+a block with more rows than the fused kernel takes, several handles in precedence order, and the
+capacity protocol; the counters as conditions on the paths taken."""
 import random
 import struct
 
@@ -11,7 +11,6 @@ import numpy as np
 import pytest
 
 from oracle import binding as ob
-from tests import blockgen as bg
 from tests import getgen, getref, sstgen
 
 pytestmark = pytest.mark.gpu
@@ -25,31 +24,10 @@ def ctx():
     return sc.Context(0)
 
 
-def check(ctx, handles, keys, ref, one_call=False):
-    """One get over `handles` equals the reference: res field by field, val_off, the value bytes.
-    one_call: a single slate_sst_get_batch call with room for the values (for the counters;
-    Context.get asks for the size first and looks the keys up twice)."""
-    rs, ref_off, ref_vals = ref[:3]
-    if one_call:
-        st, res, vals, val_off = ctx.get_into(handles, keys, len(ref_vals))
-        assert st == 0
-    else:
-        res, vals, val_off = ctx.get(handles, keys)
-    assert len(res) == len(keys)
-    for f in getref.FIELDS:
-        want = np.array([r[f] for r in rs], dtype=np.int64)
-        got = res[f].astype(np.int64)
-        bad = np.nonzero(want != got)[0]
-        assert bad.size == 0, (f, int(bad[0]), keys[int(bad[0])], rs[int(bad[0])], res[int(bad[0])])
-    assert np.array_equal(val_off, ref_off)
-    assert vals.tobytes() == ref_vals
-    return res
+check = getgen.check  # (shared with tests/test_get_shapes_gpu.py)
 
 
-def ref_of(ssts, keys):
-    consulted = set()
-    rs, vo, vals = getref.get_batch([getref.RefSst(s) for s in ssts], keys, consulted)
-    return rs, vo, vals, consulted
+ref_of = getgen.ref_of
 
 
 @pytest.mark.parametrize("codec", getgen.CODECS)
@@ -136,7 +114,7 @@ def test_index_with_stale_crc_fails_open(ctx):
     assert e.value.status == E_INDEX_CHECKSUM
 
 
-@pytest.mark.parametrize("codec", [ob.NONE, ob.SNAPPY])
+@pytest.mark.parametrize("codec", getgen.CODECS)
 def test_stale_block_crc_is_a_miss(ctx, codec):
     clean = getgen.clean_sst("random", 4096, codec)
     blocks = list(getgen.blocks_of(clean)[2])
@@ -152,16 +130,26 @@ def test_stale_block_crc_is_a_miss(ctx, codec):
     h.close()
 
 
-@pytest.mark.parametrize("codec", [ob.NONE, ob.SNAPPY])
+@pytest.mark.parametrize("codec", getgen.CODECS)
 def test_mutated_blocks(ctx, codec):
     """bg.mutate with the CRC fixed in a tenth of the blocks: flipped bits, truncation, planted
-    BE16 values, trailing bytes -- block.Decode errors, seek errors, row errors and panics."""
-    clean = getgen.clean_sst("random", 512, codec)
-    rng = random.Random(40 + codec)
-    blocks = list(getgen.blocks_of(clean)[2])
-    for b in rng.sample(range(len(blocks)), len(blocks) // 10):
-        blocks[b] = bg.mutate(rng, blocks[b], fix_crc=True)
-    sst = getgen.rebuild(clean, blocks=blocks)
+    BE16 values, trailing bytes -- block.Decode errors, seek errors, row errors and panics.  The
+    encoded bytes are mutated: under a compressing codec mostly the decompressor's errors."""
+    sst = getgen.mutated_sst(codec, "encoded")
+    keys = list(getgen.query_set("random", 512))
+    ref = ref_of([sst], keys)
+    assert sum(1 for r in ref[0] if r["err"]) >= 20
+    h = ctx.open_sst(sst)
+    check(ctx, [h], keys, ref)
+    h.close()
+
+
+@pytest.mark.parametrize("codec", getgen.CODECS[1:])
+def test_mutated_blocks_under_a_valid_frame(ctx, codec):
+    """The same mutations made to the decoded block, which is then compressed and sealed with its
+    CRC: the decompressor succeeds, and block.Decode, the seek and the row decode meet the damage
+    on every codec's general path."""
+    sst = getgen.mutated_sst(codec, "decoded")
     keys = list(getgen.query_set("random", 512))
     ref = ref_of([sst], keys)
     assert sum(1 for r in ref[0] if r["err"]) >= 20
