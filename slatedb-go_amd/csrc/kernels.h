@@ -385,6 +385,50 @@ size_t get_scan_parts(uint64_t n);
 hipError_t launch_get_val_scan(hipStream_t st, const GetQ& q, uint64_t* val_off, uint64_t* part);
 hipError_t launch_get_copy(hipStream_t st, const GetQ& q, const uint64_t* val_off, uint8_t* vals);
 
+// ---------------------------------------------------------------- sorted runs (get_runs.hip)
+// One compacted.SortedRun as the kernels see it (slate_sorted_run's device arrays, api_get.cpp).
+// The run's blocks are numbered across its SSTs: global block = blk_base[p] + b.
+struct GetRun {
+  const GetSst* views;        // n_sst: the member handles' views
+  const uint8_t* fkeys;       // the SSTs' Info.FirstKey, key p = fkeys[fk_off[p] .. fk_off[p+1])
+  const uint64_t* fk_off;     // n_sst + 1
+  const uint32_t* blk_base;   // n_sst + 1: blocks before SST p; blk_base[n_sst] = nblk
+  const uint32_t* bsst;       // nblk: the SST of a global block
+  const uint8_t* codec;       // n_sst
+  uint32_t n_sst;
+  uint32_t nblk;
+  uint32_t src;               // the run's source index in the call (n_sst of the call + r)
+};
+// A query's place in the run it is in: the SST (bit 31: from-start mode, the walk-on of
+// SortedRunIterator.Next -- block.NewIterator, no seek) beside GetQ::qblk, its global block, and
+// the run positions of the result.
+struct GetRunQ {
+  uint32_t* qsst;             // n
+  uint32_t* qgb;              // n: global block of (qsst, qblk), written by the mark kernel
+  slate_get_run_pos* pos;     // n
+};
+constexpr uint32_t kRunFromStart = 0x80000000u;
+// sort.Search over the run's first keys, the chosen SST's filter and index seek, for the active
+// queries: a stage, or qsst / qblk and an entry of pend (cnt[kGcPend]).  One launch per run.
+hipError_t launch_get_run_locate(hipStream_t st, const GetRun& run, const GetQ& q, const GetRunQ& rq,
+                                 const uint32_t* act, uint64_t na, uint32_t* pend, uint32_t* cnt);
+// the fused path over pend: as launch_get_fused, walking on through the run's SSTs; a query that
+// meets a block over 2 048 rows or an SST of another codec goes to gen with its state
+hipError_t launch_get_run_fused(hipStream_t st, const GetRun& run, const GetQ& q, const GetRunQ& rq,
+                                const uint32_t* pend, uint32_t np, uint32_t* gen, uint32_t* cnt, int num_cus);
+// general path over the run's global blocks (bflag / bdata / bmeta / list sized by run.nblk): mark
+// steps queries over ended SSTs and finishes those past the last; compact takes the blocks of one
+// codec; launch_get_publish is shared; fetch seeks (or not, from-start), fetches and steps
+hipError_t launch_get_run_mark(hipStream_t st, const GetRun& run, const GetQ& q, const GetRunQ& rq,
+                               const uint32_t* pend, uint32_t np, uint32_t* bflag);
+hipError_t launch_get_run_compact(hipStream_t st, const GetRun& run, uint32_t codec, const uint32_t* bflag,
+                                  uint32_t* list, uint64_t* in_off, uint32_t* cnt);
+hipError_t launch_get_run_gather(hipStream_t st, const GetRun& run, const uint32_t* list, const uint64_t* in_off,
+                                 uint32_t nc, uint8_t* gin);
+hipError_t launch_get_run_fetch(hipStream_t st, const GetRun& run, const GetQ& q, const GetRunQ& rq,
+                                const uint32_t* pend, uint32_t np, const uint64_t* bdata, const slate_block_meta* bmeta,
+                                slate_seek* seek, uint32_t* pend_next, uint32_t* cnt);
+
 // CodecLz4 index / filter payloads split by (independent) data block: blk = nblk x (frame offset,
 // block size word); one wave per block in LDS; sizes[k] = decoded bytes at slots + k * 64 KiB, or
 // ~0u for a block the serial path must decode (decode.hip).

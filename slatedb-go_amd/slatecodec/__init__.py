@@ -43,6 +43,9 @@ META_DTYPE = np.dtype([("status", "<i2"), ("flags", "<u2"), ("detail", "<i4"), (
 GET_DTYPE = np.dtype([("outcome", "u1"), ("stage", "u1"), ("err", "<i2"), ("sst", "<u4"), ("err_sst", "<u4"),
                       ("block", "<u4"), ("row", "<u4"), ("value_len", "<u4")])
 GET_MISS, GET_VALUE, GET_TOMBSTONE, GET_PANIC = 0, 1, 2, 3
+# slate_get_run_pos (8 bytes), parallel to GET_DTYPE
+GET_POS_DTYPE = np.dtype([("run_sst", "<u4"), ("err_run_sst", "<u4")])
+E_RUN_FIRSTKEY_PANIC = 65
 GET_AT_RANGE, GET_AT_FILTER, GET_AT_END, GET_AT_ERROR, GET_AT_ROW = 0, 1, 2, 3, 4
 ROW_DTYPE = np.dtype([("row_off", "<u4"), ("key_prefix_len", "<u2"), ("key_suffix_len", "<u2"),
                       ("value_len", "<u4"), ("flags", "u1"), ("meta_len", "u1"), ("status", "<i2")])
@@ -169,6 +172,11 @@ _SIGS = {
                                         C.POINTER(C.c_int), u64p]),
     "slate_sst_get_batch": (C.c_int, [vp, C.POINTER(vp), C.c_uint32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp]),
     "slate_sst_get_counters": (C.c_int, [vp, u64p, u64p, u64p, u64p, C.c_int]),
+    "slate_sorted_run_create": (C.c_int, [vp, C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
+    "slate_sorted_run_free": (None, [vp]),
+    "slate_sorted_run_info": (C.c_int, [vp, C.POINTER(C.c_uint32), u64p, u64p]),
+    "slate_sst_get_batch_runs": (C.c_int, [vp, C.POINTER(vp), C.c_uint32, C.POINTER(vp), C.c_uint32, vp, vp,
+                                           C.c_uint64, vp, vp, vp, C.c_uint64, vp]),
     "slate_rows_kv_lengths_device": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     "slate_rows_kv_copy_device": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     "slate_kv_gather_lengths_device": (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]),
@@ -366,6 +374,39 @@ class Context:
             st, res, vals, val_off = self.get_into(handles, keys, int(val_off[len(keys)]))
         _check(st, "slate_sst_get_batch")
         return res, vals[: int(val_off[len(keys)])], val_off
+
+    def open_run(self, handles: list["SstHandle"]) -> "SortedRun":
+        """slate_sorted_run_create: a compacted.SortedRun over opened SSTs in SSTList order."""
+        return SortedRun(self, handles)
+
+    def get_runs_into(self, handles: list["SstHandle"], runs: list["SortedRun"], keys: list[bytes],
+                      vals_cap: int | None, want_pos: bool = True):
+        """slate_sst_get_batch_runs with a caller-chosen value capacity (None: no value buffer) ->
+        (status, res, pos, vals, val_off); want_pos False passes pos = NULL (pos comes back None)."""
+        kd, ko = _arena(keys)
+        n = len(keys)
+        res = np.zeros(max(n, 1), GET_DTYPE)
+        pos = np.zeros(max(n, 1), GET_POS_DTYPE)
+        val_off = np.zeros(n + 1, np.uint64)
+        vals = np.zeros(max(vals_cap or 0, 1), np.uint8)
+        hs = (vp * max(len(handles), 1))(*[h.handle for h in handles])
+        rs = (vp * max(len(runs), 1))(*[r.handle if r is not None else None for r in runs])  # None: a NULL entry
+        st = lib().slate_sst_get_batch_runs(self._h, hs, len(handles), rs, len(runs), _ptr(kd), _ptr(ko), n, _ptr(res),
+                                            _ptr(pos) if want_pos else None,
+                                            _ptr(vals) if vals_cap is not None else None, vals_cap or 0, _ptr(val_off))
+        return st, res[:n], (pos[:n] if want_pos else None), vals[: vals_cap or 0], val_off
+
+    def get_runs(self, handles: list["SstHandle"], runs: list["SortedRun"], keys: list[bytes]):
+        """DB.Get's SST part for every key: the L0 `handles` in precedence order, then the sorted
+        `runs` in list order -> (res GET_DTYPE[n], pos GET_POS_DTYPE[n], vals u8, val_off u64[n + 1])."""
+        per_key = max(128, getattr(self, "_get_bytes_per_key", 0))
+        st, res, pos, vals, val_off = self.get_runs_into(handles, runs, keys, per_key * len(keys))
+        if keys:
+            self._get_bytes_per_key = -(-int(val_off[len(keys)]) // len(keys))
+        if st == E_CAPACITY:  # the exact size is in val_off[n]; the keys are looked up again
+            st, res, pos, vals, val_off = self.get_runs_into(handles, runs, keys, int(val_off[len(keys)]))
+        _check(st, "slate_sst_get_batch_runs")
+        return res, pos, vals[: int(val_off[len(keys)])], val_off
 
     def get_counters(self, reset: bool = False) -> dict:
         """slate_sst_get_counters -> {n_fused, n_general, n_rounds, n_blocks_decoded}."""
@@ -766,6 +807,40 @@ class Index:
             _check(lib().slate_index_block_meta(self._h, i, C.byref(off), C.byref(p), C.byref(ln)), "block_meta")
             out.append((off.value, C.string_at(p.value, ln.value) if ln.value else b""))
         return out
+
+
+class SortedRun:
+    """slate_sorted_run: a compacted.SortedRun over opened SSTs (Context.open_run).  It keeps its
+    handles alive: the run borrows them."""
+
+    def __init__(self, ctx: "Context", handles: list["SstHandle"]):
+        self._handles = list(handles)
+        hs = (vp * max(len(handles), 1))(*[h.handle for h in handles])
+        r = vp()
+        _check(lib().slate_sorted_run_create(ctx.handle, hs, len(handles), C.byref(r)), "slate_sorted_run_create")
+        self._h = r.value
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        """slate_sorted_run_info -> {n_sst, n_blocks, device_bytes}."""
+        ns, nb, db = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(lib().slate_sorted_run_info(self._h, C.byref(ns), C.byref(nb), C.byref(db)), "slate_sorted_run_info")
+        return dict(n_sst=ns.value, n_blocks=nb.value, device_bytes=db.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().slate_sorted_run_free(self._h)
+            self._h = None
+        self._handles = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except (TypeError, AttributeError):  # interpreter shutdown: module globals already gone
+            pass
 
 
 class SstHandle:

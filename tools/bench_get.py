@@ -13,7 +13,17 @@ Per codec, three JSON lines from the same run on the same box:
                (it stops at the seek: the row fetch and key compare are left to the caller);
   oracle       tests/getref.py on one thread over a sample (Python composing the C oracle).
 --check compares 10 000 sampled queries of the get_batch run with tests/getref.py.
-usage: python tools/bench_get.py [--kvs 1000000] [--queries 1000000] [--steps 5] [--check] [--out FILE]"""
+--runs measures sorted runs instead: the same KVs as one run of S SSTs (S = 1, 64, 512, or --run-ssts),
+per codec and S one JSON line with, each as the median of the steps after warm-up with min and max:
+  (a) runs      slate_sst_get_batch_runs over the run (and again with pos = NULL, which saves the
+                download of 8 bytes per query);
+  (b) per_sst   what a caller could do without it: a host bisect over the SSTs' first keys, the keys
+                grouped per SST, one slate_sst_get_batch per SST (no walk-on; the grouping is timed,
+                scattering the results back is not);
+  (c) one_sst   slate_sst_get_batch over the same KVs as one SST, the floor;
+and with --check 10 000 sampled queries of (a) against tests/srref.py.
+usage: python tools/bench_get.py [--kvs 1000000] [--queries 1000000] [--steps 5] [--check] [--out FILE]
+       python tools/bench_get.py --runs [--run-ssts 1,64,512] [--check] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -40,14 +50,22 @@ def key_array(ids: np.ndarray) -> np.ndarray:
     return out
 
 
-def build_sst(ob, n: int, codec: int, seed: int = 7) -> bytes:
-    rng = np.random.default_rng(seed)
-    keys = key_array(np.arange(n, dtype=np.uint64) * 2)
-    vals = rng.integers(0, 256, (n, 84), dtype=np.uint8)
+_WORKLOAD = {}
+
+
+def build_sst(ob, n: int, codec: int, seed: int = 7, lo: int = 0, hi: int | None = None) -> bytes:
+    """The workload's KVs [lo, hi) (default: all n) as one SST."""
+    hi = n if hi is None else hi
+    if (n, seed) not in _WORKLOAD:  # (one workload per process: the --runs leg cuts it many times)
+        _WORKLOAD.clear()
+        _WORKLOAD[(n, seed)] = (key_array(np.arange(n, dtype=np.uint64) * 2),
+                                np.random.default_rng(seed).integers(0, 256, (n, 84), dtype=np.uint8))
+    keys, vals = (x[lo:hi] for x in _WORKLOAD[(n, seed)])
+    m = hi - lo
     b = ob.SstBuilder(4096, 0, 10, codec)
-    ko = np.arange(n + 1, dtype=np.uint64) * 16
-    vo = np.arange(n + 1, dtype=np.uint64) * 84
-    assert b.add_batch(keys.reshape(-1), ko, vals.reshape(-1), vo) == 0
+    ko = np.arange(m + 1, dtype=np.uint64) * 16
+    vo = np.arange(m + 1, dtype=np.uint64) * 84
+    assert b.add_batch(np.ascontiguousarray(keys).reshape(-1), ko, np.ascontiguousarray(vals).reshape(-1), vo) == 0
     assert b.build() == 0
     return b.encode_table()
 
@@ -57,8 +75,116 @@ def median(xs):
     return xs[len(xs) // 2]
 
 
+def stats(ts):
+    return {"ms": round(median(ts) * 1e3, 3), "min_ms": round(min(ts) * 1e3, 3), "max_ms": round(max(ts) * 1e3, 3)}
+
+
+def runs_leg(args, ctx, sc, ob, qk, qo, ids):
+    """The --runs measurement (see the module's docstring) -> (lines, ok)."""
+    from tests import getref, srref
+    L = sc.lib()
+    n, nq = args.kvs, args.queries
+    lines, ok = [], True
+    res = np.zeros(nq, sc.GET_DTYPE)
+    pos = np.zeros(nq, sc.GET_POS_DTYPE)
+    val_off = np.zeros(nq + 1, np.uint64)
+    vals = np.zeros(84 * nq + 16, np.uint8)
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        ts = []
+        for _ in range(args.steps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return ts
+
+    for codec, cname in ((sc.NONE, "none"), (sc.SNAPPY, "snappy")):
+        one = ctx.open_sst(build_sst(ob, n, codec))
+        h1 = (C.c_void_p * 1)(one.handle)
+
+        def floor():
+            st = L.slate_sst_get_batch(ctx.handle, h1, 1, sc._ptr(qk), sc._ptr(qo), nq, sc._ptr(res), sc._ptr(vals),
+                                       vals.size, sc._ptr(val_off))
+            assert st == sc.OK, st
+
+        for S in args.run_ssts:
+            step = -(-n // S)
+            cuts = [(p * step, min(n, (p + 1) * step)) for p in range(S) if p * step < n]
+            ssts = [build_sst(ob, n, codec, lo=lo, hi=hi) for lo, hi in cuts]
+            hs = [ctx.open_sst(s) for s in ssts]
+            run = ctx.open_run(hs)
+            rp = (C.c_void_p * 1)(run.handle)
+            first_ids = np.array([2 * lo for lo, _ in cuts], dtype=np.uint64)
+
+            def runs(with_pos=True):
+                st = L.slate_sst_get_batch_runs(ctx.handle, None, 0, rp, 1, sc._ptr(qk), sc._ptr(qo), nq, sc._ptr(res),
+                                                sc._ptr(pos) if with_pos else None, sc._ptr(vals), vals.size,
+                                                sc._ptr(val_off))
+                assert st == sc.OK, st
+
+            def per_sst():
+                # the keys are b"k%015d" % id: a bisect over the first keys is one over their ids
+                which = np.searchsorted(first_ids, ids, side="right").astype(np.int64) - 1
+                order = np.argsort(which, kind="stable")
+                sk = np.ascontiguousarray(qk.reshape(-1, 16)[order])
+                bounds = np.searchsorted(which[order], np.arange(len(cuts) + 1))
+                vo = 0
+                for p in range(len(cuts)):
+                    a, b = int(bounds[p]), int(bounds[p + 1])
+                    if a == b:
+                        continue
+                    hp = (C.c_void_p * 1)(hs[p].handle)
+                    st = L.slate_sst_get_batch(ctx.handle, hp, 1, sc._ptr(sk[a:b]), sc._ptr(qo), b - a,
+                                               sc._ptr(res[a:b]), sc._ptr(vals[vo:]), vals.size - vo, sc._ptr(val_off[a:]))
+                    assert st == sc.OK, st
+                    vo += int(val_off[a + b - a])
+
+            ctx.get_counters(reset=True)
+            ta = timed(runs)
+            cnt = {k: v // (args.steps + args.warmup) for k, v in ctx.get_counters(reset=True).items()}
+            found = int((res["outcome"] == sc.GET_VALUE).sum())
+            line = {"metric": f"batched point reads over one sorted run of {len(cuts)} SSTs, codec {cname}",
+                    "config": {"kvs": n, "queries": nq, "ssts": len(cuts), "blocks": run.info()["n_blocks"],
+                               "run_device_bytes": run.info()["device_bytes"], "steps": args.steps},
+                    "runs": stats(ta), "counters": cnt, "found": found}
+            if args.check:
+                refs = [getref.RefSst(s) for s in ssts]
+                pick = np.random.default_rng(2).choice(nq, min(10_000, nq), replace=False)
+                bad = 0
+                for i in pick:
+                    r = srref.get_one([], [refs], qk[16 * i:16 * i + 16].tobytes())
+                    got = vals[int(val_off[i]):int(val_off[i + 1])].tobytes()
+                    bad += (any(int(res[f][i]) != r[f] for f in getref.FIELDS) or got != r["value"]
+                            or int(pos["run_sst"][i]) != r["run_sst"] or int(pos["err_run_sst"][i]) != r["err_run_sst"])
+                line["check"] = {"sampled": int(len(pick)), "mismatches": int(bad)}
+                ok = ok and bad == 0
+            tb = timed(per_sst)
+            tc = timed(floor)
+            line.update(runs_pos_null=stats(timed(lambda: runs(False))), per_sst=stats(tb), one_sst=stats(tc),
+                        runs_over_per_sst=round(median(ta) / median(tb), 3),
+                        runs_over_one_sst=round(median(ta) / median(tc), 3),
+                        ranges_overlap_runs_per_sst=bool(min(ta) <= max(tb) and min(tb) <= max(ta)),
+                        value=round(nq / median(ta)), unit="queries/s")
+            lines.append(line)
+            print(json.dumps(line), flush=True)
+            if args.out:
+                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+                with open(args.out, "w") as f:
+                    for ln in lines:
+                        f.write(json.dumps(ln) + "\n")
+            run.close()
+            for h in hs:
+                h.close()
+        one.close()
+    return lines, ok
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", action="store_true", help="measure sorted runs (slate_sst_get_batch_runs)")
+    ap.add_argument("--run-ssts", type=lambda s: [int(x) for x in s.split(",")], default=[1, 64, 512])
     ap.add_argument("--kvs", type=int, default=1_000_000)
     ap.add_argument("--queries", type=int, default=1_000_000)
     ap.add_argument("--steps", type=int, default=5)
@@ -82,6 +208,9 @@ def main():
     qo = np.arange(nq + 1, dtype=np.uint64) * 16
     lines = []
     ok = True
+    if args.runs:
+        lines, ok = runs_leg(args, ctx, sc, ob, qk, qo, ids)
+        sys.exit(0 if ok else 1)
     for codec, cname in ((sc.NONE, "none"), (sc.SNAPPY, "snappy")):
         sst = build_sst(ob, n, codec)
         a = np.frombuffer(sst, dtype=np.uint8)
